@@ -7,8 +7,17 @@ synthesised and framed on the device (splitmix64 payloads).  Ranks are
 independent WAL streams, one per GPU, no collective on the data path
 ("scaling": "weak"); the barrier / max-over-ranks uses gloo on the host.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run does what the headline needs and no more: synthesise the blocks,
+warm up, time the K steps, print the line.  `--dump-outputs DIR` then also
+writes what the last timed step computed (every block's masked CRC and verify
+flag; a fixed sample of the blocks where all ranks' files would pass 64 MB,
+dump_sample) as DIR/<name>.npy; the inputs depend on the arguments alone, so two
+builds can be compared output for output.  `--full` adds the other legs
+(`cpu_baseline`, `end_to_end`, `c3`, `c3_small`; each has its own switch
+below); without it those fields are null.
 
 `--gpus N` with N > 1 outside torch.distributed (no WORLD_SIZE) launches the N
 ranks itself: before anything touches a GPU it counts the visible gfx950
@@ -18,7 +27,7 @@ script as a child process and exits with its return code.  Each rank drives
 GPU `LOCAL_RANK`; the JSON's `ranks` names every rank's device and PCI bus id
 with its own kernel time, so a record shows that N distinct GPUs ran.
 
-Prints one JSON line on rank 0.  The `cpu_baseline` leg (rank 0, N=1) times
+Prints one JSON line on rank 0.  The `cpu_baseline` leg (--full, rank 0, N=1) times
 the oracle's bytewise table CRC -- the reference crate's algorithm class --
 on a bounded sample of the same blocks, on one host core, and checks the
 GPU's CRCs for that sample against it.
@@ -52,6 +61,12 @@ def parse(argv=None):
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--blocks", type=int, default=1 << 20, help="blocks per rank (default 1M = 32 GiB)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (masked CRC and verify flag of every block) "
+                         "as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: cpu_baseline, end_to_end, c3, c3_small "
+                         "(the options below size or skip them)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="bound on the CPU baseline leg")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--variant", type=int, default=None, help="experiment kernel variant (default: production)")
@@ -641,6 +656,39 @@ def c3_records(ctx, D, gib: float, iters: int = 9, shape: str = "zipf"):
     }
 
 
+# array bytes of one --dump-outputs, all ranks' files together: under 64 MB with their .npy headers
+DUMP_MAX_BYTES = 60_000_000
+DUMP_BLOCK_BYTES = 8 + 4     # a block's float64 CRC + float32 flag
+
+
+def dump_sample(nblocks: int, world: int = 1):
+    """The blocks of a rank that --dump-outputs writes: None = all of them,
+    else the ascending indices of a fixed sample (seeded by SEED alone, the same
+    on every rank and run) of DUMP_MAX_BYTES / DUMP_BLOCK_BYTES / world blocks,
+    so that the files of all ranks stay within DUMP_MAX_BYTES.  No index file
+    is written: a reader of the dump calls this with the run's arguments."""
+    cap = DUMP_MAX_BYTES // DUMP_BLOCK_BYTES // world
+    if nblocks <= cap:
+        return None
+    return np.sort(np.random.default_rng(SEED).choice(nblocks, cap, replace=False))
+
+
+def dump_outputs(ctx, D, path: str, masked_dev, ok_dev, nblocks: int):
+    """--dump-outputs: what crc_full_blocks left in its output buffers after
+    the last timed step, as <path>/masked_crc.npy (float64: a u32 is exact in
+    it) and <path>/verify_ok.npy (float32, 0 / 1), with `_rank<r>` before the
+    extension when there are several ranks; of the blocks dump_sample names."""
+    masked = ctx.d2h(masked_dev, 4 * nblocks, np.uint32)
+    ok = ctx.d2h(ok_dev, nblocks)
+    idx = dump_sample(nblocks, D.world)
+    if idx is not None:
+        masked, ok = masked[idx], ok[idx]
+    os.makedirs(path, exist_ok=True)
+    suffix = f"_rank{D.rank}" if D.world > 1 else ""
+    np.save(os.path.join(path, f"masked_crc{suffix}.npy"), masked.astype(np.float64))
+    np.save(os.path.join(path, f"verify_ok{suffix}.npy"), ok.astype(np.float32))
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     args = parse(argv)
@@ -702,8 +750,12 @@ def main(argv=None):
     traffic, traffic_source = pmc_traffic(n)
 
     progress(D, f"C2 {kern_ms_max:.3f} ms per launch")
+    if args.dump_outputs:
+        dump_outputs(ctx, D, args.dump_outputs, masked, ok, n)
+
+    # every leg below is beside the headline: --full only
     e2e = None
-    e2e_gib = e2e_share(args, D)
+    e2e_gib = e2e_share(args, D) if args.full else 0
     if e2e_gib > 0:
         progress(D, f"end_to_end: writing and replaying a {e2e_gib:g} GiB-per-rank WAL file")
         e2e = end_to_end(ctx, D, dblocks, n, e2e_gib)
@@ -712,16 +764,16 @@ def main(argv=None):
         progress(D, f"end_to_end: {e2e.get('value')} GiB/s")
 
     c3 = None
-    if args.c3_gib > 0:
+    if args.full and args.c3_gib > 0:
         c3 = c3_records(ctx, D, args.c3_gib)
         progress(D, f"c3: {c3['ms']} ms")
     c3_small = None
-    if args.c3_small_gib > 0:
+    if args.full and args.c3_small_gib > 0:
         c3_small = c3_records(ctx, D, args.c3_small_gib, shape="small")
         progress(D, f"c3_small: {c3_small['ms']} ms")
 
     cpu = None
-    if D.rank == 0 and D.world == 1 and not args.no_cpu:
+    if args.full and D.rank == 0 and D.world == 1 and not args.no_cpu:
         progress(D, "cpu_baseline")
         cpu = cpu_baseline(ctx, dblocks, masked, n, args.cpu_seconds)
 
@@ -788,13 +840,17 @@ def result_line(args, D, ranks, value, ms):
 
 def dry_run(args, D):
     """The launcher and the distributed plumbing without a GPU: every rank
-    reports itself, rank 0 prints the line with null values.  With --e2e-gib
-    the end_to_end leg's shared-file logic runs for real (free-space check of
-    world x per-rank bytes, every rank's part written, the all-ranks skip on
-    any failure) with zero bytes in place of the device blocks."""
+    reports itself, rank 0 prints the line with null values.  With --full and
+    an explicit --e2e-gib the end_to_end leg's shared-file logic runs for real
+    (free-space check of world x per-rank bytes, every rank's part written,
+    the all-ranks skip on any failure) with zero bytes in place of the device
+    blocks."""
     D.barrier()
     e2e = None
-    e2e_gib = e2e_share(args, D)
+    # only an explicit --e2e-gib: the default share (C5's 100 GiB file) would be 100 GiB of zeros
+    e2e_gib = args.e2e_gib if args.full and args.e2e_gib is not None else 0
+    if args.full and args.e2e_gib is None:
+        progress(D, "dry run: end_to_end not rehearsed without an explicit --e2e-gib")
     if e2e_gib > 0:
         k = int(e2e_gib * (1 << 30)) // BLOCK_SIZE
         per = k * BLOCK_SIZE

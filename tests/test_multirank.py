@@ -130,7 +130,7 @@ def test_bench_gpus_8_dry_run(tmp_path):
     rank writes its part at rank x per, all ranks see the whole file.
     Partitioning: contiguous block-aligned parts (records never cross a block,
     log_writer.rs:66-76)."""
-    d = _dry(["--gpus", "8", "--dry-run", "--blocks", "64", "--e2e-gib", str(16 * 32768 / 2**30)], devices=8,
+    d = _dry(["--gpus", "8", "--dry-run", "--full", "--blocks", "64", "--e2e-gib", str(16 * 32768 / 2**30)], devices=8,
              env_extra={"REVEL_BENCH_DIR": str(tmp_path)})
     assert d["n_gpus"] == 8 and d["dry_run"]
     assert [r["rank"] for r in d["ranks"]] == list(range(8))
@@ -146,12 +146,12 @@ def test_bench_gpus_8_e2e_skips_together(tmp_path):
     """Free space short for 8 x the per-rank part, or one rank's write
     failing: every rank skips the end_to_end leg together and the line is
     still printed."""
-    big = _dry(["--gpus", "8", "--dry-run", "--blocks", str(1 << 40), "--e2e-gib", "1000000"], devices=8,
+    big = _dry(["--gpus", "8", "--dry-run", "--full", "--blocks", str(1 << 40), "--e2e-gib", "1000000"], devices=8,
                env_extra={"REVEL_BENCH_DIR": str(tmp_path)})
     e = big["end_to_end"]
     assert e["file_bytes"] == 8 * int(1000000 * (1 << 30)) // 32768 * 32768
     assert "MiB free <" in e["skipped"] and all(r["skipped"] for r in e["per_rank"])
-    bad = _dry(["--gpus", "8", "--dry-run", "--blocks", "64", "--e2e-gib", str(4 * 32768 / 2**30)], devices=8,
+    bad = _dry(["--gpus", "8", "--dry-run", "--full", "--blocks", "64", "--e2e-gib", str(4 * 32768 / 2**30)], devices=8,
                env_extra={"REVEL_BENCH_DIR": str(tmp_path), "REVEL_BENCH_E2E_FAIL_RANK": "5"})
     e = bad["end_to_end"]
     assert e["skipped"] and all(r["skipped"] for r in e["per_rank"])

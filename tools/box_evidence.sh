@@ -2,8 +2,8 @@
 # Evidence for the build in this tree, on one MI355X box (run through gpurun):
 #   smoke, the product GPU suite, PMC FETCH_SIZE / WRITE_SIZE passes of the C2
 #   kernel and of the c3 / c3_small pipelines (-> profiles/pmc_*.json in the
-#   box's tree, so the bench below prints validated `traffic`; copies under
-#   gpurun_out/<tag>/ to commit), bench.py's default line, and a kernel trace
+#   box's tree, so the bench below prints validated `traffic`; copies in the
+#   output folder of <tag> to commit), bench.py --full's line, and a kernel trace
 #   of the c3 legs.  Every GPU step runs under its own time limit; a fault-class
 #   exit stops the script (tools/box_step.sh).
 # usage: tools/box_evidence.sh <tag>
@@ -34,7 +34,7 @@ step 60 "$O/pmc_c3_summary.log" python3 "$R/tools/pmc_summary.py" "$O/zipfpmc" -
 step 60 "$O/pmc_c3_small_summary.log" python3 "$R/tools/pmc_summary.py" "$O/smallpmc" --pipeline small \
     --image-bytes "$SB" --json "$R/profiles/pmc_c3_small.json"
 cp "$R"/profiles/pmc_c2.json "$R"/profiles/pmc_c3.json "$R"/profiles/pmc_c3_small.json "$O/"
-step 900 "$O/bench.log" python3 "$R/bench.py"
+step 900 "$O/bench.log" python3 "$R/bench.py" --full
 step 300 "$O/c3_trace.log" rocprofv3 --kernel-trace --stats -d "$O/c3_trace" -o c3 -f csv -- \
     python3 "$R/tools/c3_legs.py"
 rm -rf "$O/c2pmc" "$O/zipfpmc" "$O/smallpmc"

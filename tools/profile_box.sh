@@ -10,7 +10,7 @@ mkdir -p "$O"
 export TMPDIR=/tmp
 step() { "$R/tools/box_step.sh" "$@" || exit 99; }
 step 120 "$O/counters_list.log" rocprofv3 -L
-step 300 "$O/bench_trace.log" rocprofv3 --kernel-trace --stats -d "$O/bench_trace" -o bench -f csv -- python3 "$R/bench.py" --steps 10 --warmup 2 --no-cpu
+step 300 "$O/bench_trace.log" rocprofv3 --kernel-trace --stats -d "$O/bench_trace" -o bench -f csv -- python3 "$R/bench.py" --full --steps 10 --warmup 2 --no-cpu
 W="python3 $R/tools/variants.py --variants $variants --rounds 1 --iters 2"
 i=0
 for grp in "FETCH_SIZE" "WRITE_SIZE" \
