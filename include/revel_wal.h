@@ -338,6 +338,40 @@ int revel_gpu_decode_batches(revel_gpu_context* ctx, const void* d_payload, uint
                              const revel_logical_record* d_logical, size_t nlogical, revel_batch_info* d_info,
                              revel_batch_entry* d_entries, size_t entries_cap, uint64_t* nentries, void* stream);
 
+/* ---- device WriteBatch encode (the write side of the decode above) -------
+ * write_batch.rs:44-55,67-69,160-166 + db.rs:103-108 for a whole table of batches.
+ * Takes the tables revel_gpu_decode_batches produces, or tables of the same
+ * layout built by the caller; key and value offsets point into d_data
+ * (data_bytes bytes).  Rep b encodes entries [first_entry, first_entry +
+ * nentries) of d_info[b] in order: rep[0:8] = d_info[b].sequence (LE),
+ * rep[8:12] = d_info[b].nentries (what that many put / delete calls leave in
+ * the count), then per entry the tag byte (type), the minimal varint32 of
+ * key_len (coding.rs:18-49), the key, and for REVEL_TYPE_VALUE the minimal
+ * varint32 of value_len and the value (a deletion's value fields are ignored).
+ * d_info[b].status / .count and each entry's .sequence / .batch are ignored; a
+ * batch with nentries == 0 is its 12-byte header.  Entries that no batch
+ * covers are not encoded.
+ * Reps are written back to back into d_reps (capacity reps_cap) in batch
+ * order; lens (HOST memory, nbatches entries: the array revel_log_framed_size
+ * and revel_gpu_append_records take) receives each rep's length and
+ * *reps_bytes their sum.  Returns when done.
+ * Sizing: with d_reps == NULL and reps_cap == 0 only lens and *reps_bytes are
+ * produced (REVEL_OK).  Otherwise *reps_bytes > reps_cap returns
+ * REVEL_INVALID_ARGUMENT with lens and *reps_bytes set and d_reps untouched.
+ * The caller guarantees that the batches' entry ranges are pairwise disjoint
+ * and that d_reps does not overlap d_data.  Checked on the device, before any
+ * byte is copied, and returned as REVEL_INVALID_ARGUMENT (revel_last_error()
+ * names the lowest bad batch, or else the lowest bad entry; d_reps contents
+ * are then unspecified, nothing out of range is read or written): an entry
+ * range past nentries, and for every entry of the table a type other than 0 / 1
+ * or a key or value span outside [0, data_bytes).  Keys and values are read
+ * in aligned 4-byte words that hold at least one of their bytes. */
+int revel_gpu_encode_batches(revel_gpu_context* ctx, const void* d_data, uint64_t data_bytes,
+                             const revel_batch_entry* d_entries, size_t nentries,
+                             const revel_batch_info* d_info, size_t nbatches,
+                             void* d_reps, uint64_t reps_cap, uint64_t* lens, uint64_t* reps_bytes,
+                             void* stream);
+
 /* ---- device append framing (log_writer.rs:58-124 for a whole batch) ----- */
 /* Bytes that n successive add_record calls starting at block_offset would
  * append (headers, payloads, zero trailers). */

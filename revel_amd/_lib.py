@@ -149,6 +149,8 @@ SIGNATURES = {
                                      c_void_p, POINTER(c_uint64), POINTER(c_uint64), c_void_p]),
     "revel_gpu_decode_batches": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_size_t, c_void_p, c_void_p,
                                          c_size_t, POINTER(c_uint64), c_void_p]),
+    "revel_gpu_encode_batches": (c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_size_t, c_void_p, c_size_t,
+                                         c_void_p, c_uint64, c_void_p, POINTER(c_uint64), c_void_p]),
     "revel_log_framed_size": (c_uint64, [c_void_p, c_size_t, c_uint64]),
     "revel_gpu_append_records": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, POINTER(c_uint64), c_void_p,
                                          c_size_t, POINTER(c_size_t), c_void_p]),
@@ -184,6 +186,9 @@ EXTRA_SIGNATURES = {
                                               c_void_p, c_void_p]),
     "revel_debug_check_record_index": (c_int, [c_void_p, c_void_p, c_size_t]),
 }
+
+# entry points an older build loaded for an A/B run (bench tools' --lib) may lack
+NEWER_SYMBOLS = {"revel_gpu_encode_batches"}
 
 # tools/experiments/libexperiments.so: kernel variants kept for the record
 EXPERIMENT_PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", "experiments",
@@ -241,8 +246,8 @@ def lib() -> ctypes.CDLL:
                 "`python -c 'import __graft_entry__ as g; g.build()'` (there is no fallback)")
         L = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in {**SIGNATURES, **EXTRA_SIGNATURES}.items():
-            if name in EXTRA_SIGNATURES and not hasattr(L, name):
-                continue  # a test / A-B hook an older build (tools/ab_libs_c3.sh) does not export
+            if (name in EXTRA_SIGNATURES or name in NEWER_SYMBOLS) and not hasattr(L, name):
+                continue  # a test / A-B hook or newer entry point an older build (tools/ab_libs_c3.sh) does not export
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

@@ -53,6 +53,11 @@ void destroy_context(revel_gpu_context* ctx) {
         (void)hipStreamSynchronize(ctx->stream);
         (void)hipStreamDestroy(ctx->stream);
     }
+    if (ctx->enc_copy) {
+        (void)hipStreamSynchronize(ctx->enc_copy);
+        (void)hipStreamDestroy(ctx->enc_copy);
+    }
+    if (ctx->enc_lens_ready) (void)hipEventDestroy(ctx->enc_lens_ready);
     if (ctx->hlist) (void)hipFree(ctx->hlist);
     if (ctx->scan_scratch) (void)hipFree(ctx->scan_scratch);
     if (ctx->wsums) (void)hipFree(ctx->wsums);

@@ -137,8 +137,26 @@ hipError_t batch_emit(const DeviceInfo& di, const void* d_payload, uint64_t payl
                       const revel_logical_record* d_logical, uint64_t n, const uint64_t* d_first,
                       revel_batch_info* d_info, revel_batch_entry* d_entries, uint64_t cap, hipStream_t st);
 
+// Device WriteBatch encode (batch_encode.hip).  *d_err (preset to ~0) takes
+// the lowest bad index: a batch's, or with bit 63 set an entry's when every
+// batch range is good.  encode_sizes: d_sizes[i] = encoded bytes of entry i,
+// d_sizes[nentries] = 0.  encode_lengths: d_blen[b] = rep bytes of batch b from
+// d_E, the exclusive scan of the sizes; d_blen[nbatches] = 0.  encode_emit:
+// headers, then keys and values; d_roff = the exclusive scan of d_blen (its
+// last element the total), d_ent_dst = nentries u64 preset to ~0, d_hdr_seq /
+// d_hdr_n = nentries u64 / u32 of scratch (the header fields, at each batch's first entry).  It writes
+// nothing when *d_err is set or the total exceeds cap.
+hipError_t encode_sizes(const DeviceInfo& di, const revel_batch_entry* d_entries, uint64_t nentries,
+                        uint64_t data_bytes, uint64_t* d_sizes, uint64_t* d_err, hipStream_t st);
+hipError_t encode_lengths(const DeviceInfo& di, const revel_batch_info* d_info, uint64_t nbatches, uint64_t nentries,
+                          const uint64_t* d_E, uint64_t* d_blen, uint64_t* d_err, hipStream_t st);
+hipError_t encode_emit(const DeviceInfo& di, const void* d_data, const revel_batch_entry* d_entries, uint64_t nentries,
+                       const revel_batch_info* d_info, uint64_t nbatches, const uint64_t* d_E, const uint64_t* d_roff,
+                       const uint64_t* d_err, uint64_t cap, uint64_t* d_ent_dst, uint64_t* d_hdr_seq, uint32_t* d_hdr_n,
+                       void* d_reps, hipStream_t st);
+
 // Grow-only device scratch owned by a revel_gpu_context.  The C-ABI calls
-// that use it (decode_batches, reassemble, append framing) synchronise their
+// that use it (decode_batches, encode_batches, reassemble, append framing) synchronise their
 // stream before returning, so one call's scratch is free for the next; a call
 // that fails synchronises too before it returns.
 struct ScratchArena {
@@ -287,6 +305,10 @@ struct revel_gpu_context {
         uint8_t* h[kSlots] = {};
         hipEvent_t e0[kSlots] = {}, e1[kSlots] = {};
     } shard_ring;
+    // revel_gpu_encode_batches' second stream and event (created on first use):
+    // the read-back of the per-rep lengths runs beside the header and emit kernels
+    hipStream_t enc_copy = nullptr;
+    hipEvent_t enc_lens_ready = nullptr;
     // Lifetime: live readers pin the context; revel_gpu_context_free with
     // readers still alive only marks it, and the last reader's release
     // destroys it (revel_wal.h, "GPU context").

@@ -315,6 +315,31 @@ class GpuContext:
                                              ent.ptr, cap, ctypes.byref(ne), None))
         return info, ent, ne.value
 
+    # ---- device WriteBatch encode ----
+    def encode_batches_device(self, data: DeviceBuffer, data_bytes: int, entries: DeviceBuffer, nentries: int,
+                              info: DeviceBuffer, nbatches: int):
+        """Build every batch's rep on the GPU from decode-shaped tables
+        (revel_gpu_encode_batches: a sizing call, then the encode):
+        (reps DeviceBuffer, lens np.uint64 array, reps_bytes)."""
+        L = lib()
+        lens = np.zeros(nbatches, dtype=np.uint64)
+        total = ctypes.c_uint64()
+        args = (self._h, data.ptr, data_bytes, entries.ptr, nentries, info.ptr, nbatches)
+        check(L.revel_gpu_encode_batches(*args, None, 0, lens.ctypes.data, ctypes.byref(total), None))
+        reps = self.alloc(max(1, total.value))
+        if nbatches:
+            check(L.revel_gpu_encode_batches(*args, reps.ptr, total.value, lens.ctypes.data, ctypes.byref(total),
+                                             None))
+        return reps, lens, total.value
+
+    def write_batches(self, data: DeviceBuffer, data_bytes: int, entries: DeviceBuffer, nentries: int,
+                      info: DeviceBuffer, nbatches: int, block_offset: int = 0):
+        """DB::write (db.rs:95-112) for a table of batches, in HBM: encode the
+        reps, then frame them as successive add_record calls would; returns
+        (image DeviceBuffer, image_len, new block_offset)."""
+        reps, lens, _ = self.encode_batches_device(data, data_bytes, entries, nentries, info, nbatches)
+        return self.append_records(reps, lens, block_offset)
+
     def replay_batches(self, image: DeviceBuffer, nbytes: int, base_offset: int = 0, checksum: bool = True):
         """WAL image in HBM -> verified, reassembled, decoded WriteBatches.
         Returns (events, payload, infos BATCH_INFO_DTYPE, entries

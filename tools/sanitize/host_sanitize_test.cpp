@@ -301,6 +301,9 @@ int main() {
     CHECK(revel_gpu_replay_file(nullptr, nullptr, 0, 0, 0, 0, 0, 0, &st) != REVEL_OK);
     uint64_t ne = 0;
     CHECK(revel_gpu_decode_batches(nullptr, nullptr, 0, nullptr, 0, nullptr, nullptr, 0, &ne, nullptr) != REVEL_OK);
+    uint64_t el = 0, eb = 7;
+    CHECK(revel_gpu_encode_batches(nullptr, nullptr, 0, nullptr, 0, nullptr, 1, nullptr, 0, &el, &eb, nullptr) ==
+          REVEL_INVALID_ARGUMENT);
     uint64_t nl = 0, pb = 0;
     CHECK(revel_gpu_reassemble(nullptr, nullptr, 0, 0, nullptr, 0, 1, nullptr, nullptr, &nl, &pb, nullptr) != REVEL_OK);
     CHECK(revel_last_error() != nullptr);
