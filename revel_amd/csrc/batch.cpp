@@ -17,9 +17,8 @@ extern "C" int revel_gpu_decode_batches(revel_gpu_context* ctx, const void* d_pa
     if (nlogical == 0) return REVEL_OK;
     if (!d_payload || !d_logical || !d_info || (entries_cap && !d_entries))
         return set_error(REVEL_INVALID_ARGUMENT, "null device buffer");
-    revel::DeviceGuard guard(ctx->di.device);
-    if (guard.err() != hipSuccess) return set_error(REVEL_IO_ERROR, "hipSetDevice failed");
-    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    CHECK_CTX(ctx);
+    hipStream_t st = revel::pick(ctx, stream);
     const uint64_t n = nlogical;
     revel::DeviceScratch S(&ctx->arena);
     uint64_t *nent, *first, *tiles;
@@ -37,7 +36,7 @@ extern "C" int revel_gpu_decode_batches(revel_gpu_context* ctx, const void* d_pa
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) {
         (void)hipStreamSynchronize(st);  // the context's scratch is free before the next call
-        return set_error(REVEL_IO_ERROR, "decode_batches: %s", hipGetErrorString(e));
+        return revel::hip_fail(e, "decode_batches");
     }
     *nentries = last_first + last_n;
     if (*nentries > entries_cap)

@@ -20,9 +20,8 @@ extern "C" int revel_gpu_encode_batches(revel_gpu_context* ctx, const void* d_da
     if (!d_info || (nentries && !d_entries) || (data_bytes && !d_data) || (reps_cap && !d_reps))
         return set_error(REVEL_INVALID_ARGUMENT, "null device buffer");
     const bool sizing = !d_reps;  // reps_cap is 0 here: lens and the total only
-    revel::DeviceGuard guard(ctx->di.device);
-    if (guard.err() != hipSuccess) return set_error(REVEL_IO_ERROR, "hipSetDevice failed");
-    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    CHECK_CTX(ctx);
+    hipStream_t st = revel::pick(ctx, stream);
     const uint64_t ne = nentries, nb = nbatches;
     revel::DeviceScratch S(&ctx->arena);
     // sizes[ne + 1] becomes the entries' destination offsets once E is scanned from it
@@ -67,7 +66,7 @@ extern "C" int revel_gpu_encode_batches(revel_gpu_context* ctx, const void* d_da
     if (e != hipSuccess) {
         (void)hipStreamSynchronize(st);  // the context's scratch is free before the next call
         if (ctx->enc_copy) (void)hipStreamSynchronize(ctx->enc_copy);
-        return set_error(REVEL_IO_ERROR, "encode_batches: %s", hipGetErrorString(e));
+        return revel::hip_fail(e, "encode_batches");
     }
     *reps_bytes = total;
     if (bad != ~0ull) {

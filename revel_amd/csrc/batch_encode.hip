@@ -14,11 +14,8 @@
 // with its destination offset and hands the header fields to the first one;
 // entries no batch covers keep the stamp ~0 and are skipped.  k_enc_emit then
 // writes the headers and copies every key
-// and value as k_reasm_gather copies fragments: 8-lane groups, spans of at
-// most kTinyCopy bytes with all of a group's loads issued before any store,
-// spans up to 1 KiB by the group, larger ones by the whole wave.  No atomics
-// on the data path (the only atomic is the error word's min, taken on bad
-// input), no LDS.
+// and value with the span engine of device_common.h.  No atomics on the data
+// path (the only atomic is the error word's min, taken on bad input), no LDS.
 //
 // Bad input never reaches a copy: the size pass checks every entry's type and
 // spans, the length pass every batch's entry range, both record the lowest bad
@@ -129,15 +126,14 @@ __global__ void k_enc_head(const revel_batch_info* __restrict__ info, uint64_t n
     }
 }
 
-// Entries, 8 * kEncEpg per wave visit, kEncEpg per 8-lane group; each entry is
-// a few header bytes (tag + varints, one byte per lane of the group) and two
-// spans, key and value.
-constexpr uint32_t kSmallSpan = 1024;
+// Entries, kEncEpg per 8-lane group and visit; each entry is a few header
+// bytes (tag + varints, one byte per lane of the group) and two spans, key and
+// value, copied by the span engine of device_common.h.
 #ifndef REVEL_ENC_EPG
 #define REVEL_ENC_EPG 2
 #endif
 // entries per 8-lane group and visit: 1 = 125 VGPRs, 4 waves per SIMD; 2 = 189 VGPRs, 2 waves per SIMD, the
-// same spans in flight per SIMD either way (206 VGPRs with the header fields).  Measured before the lengths'
+// same spans in flight per SIMD either way (still 189 with the header fields).  Measured before the lengths'
 // second stream and the header fields, the whole call on 1 GiB of 16-B keys + 100-B values: 3.20 / 3.10 ms at
 // one batch per entry, 1.66 / 1.67 ms at 100 entries per batch.
 constexpr uint32_t kEncEpg = REVEL_ENC_EPG;
@@ -149,18 +145,17 @@ __global__ __launch_bounds__(256) void k_enc_emit(const uint8_t* __restrict__ da
                                                   const uint64_t* __restrict__ total, const uint64_t* __restrict__ err,
                                                   uint64_t cap, uint8_t* __restrict__ reps) {
     if (*err != kEncNone || *total > cap) return;
+    using Visit = SpanVisit<kEncEpg>;
     const uint8_t* safe = reinterpret_cast<const uint8_t*>(err);  // 8 readable bytes for the idle lanes' loads
-    const uint32_t lane = lane_id(), grp = lane >> 3, gl = lane & 7u;
-    const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x / 64);
-    const uint64_t w0 = blockIdx.x * (uint64_t)(blockDim.x / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    constexpr uint64_t kVisit = 8u * kEncEpg;
+    const uint32_t lane = lane_id(), gl = lane & 7u;
+    const uint64_t start = Visit::first(), stride = Visit::stride();
     // descriptors one visit ahead, clamped loads + ~0 for "nothing here"
     uint64_t dst_n[kEncEpg], koff_n[kEncEpg], voff_n[kEncEpg], seq_n[kEncEpg];
     uint32_t klen_n[kEncEpg], vlen_n[kEncEpg], type_n[kEncEpg], cnt_n[kEncEpg];
     auto fetch = [&](uint64_t base) {
 #pragma unroll
         for (uint32_t j = 0; j < kEncEpg; ++j) {
-            const uint64_t k = base + 8u * j + grp;
+            const uint64_t k = Visit::index(base, j);
             const uint64_t kc = k < n ? k : n - 1;
             const uint64_t d = ent_dst[kc];
             dst_n[j] = k < n ? d : kEncNone;
@@ -173,12 +168,10 @@ __global__ __launch_bounds__(256) void k_enc_emit(const uint8_t* __restrict__ da
             cnt_n[j] = hdr_n[kc];
         }
     };
-    if (w0 * kVisit < n) fetch(w0 * kVisit);
-    for (uint64_t base = w0 * kVisit; base < n; base += waves * kVisit) {
-        // span s of entry j: 2 j = key, 2 j + 1 = value (length 0 for a deletion or a skipped entry)
-        const uint8_t* src[2 * kEncEpg];
-        uint8_t* dst[2 * kEncEpg];
-        uint32_t len[2 * kEncEpg];
+    if (start < n) fetch(start);
+    for (uint64_t base = start; base < n; base += stride) {
+        // spans of entry j, data -> reps: 2 j = key, 2 j + 1 = value (dead for a deletion or a skipped entry)
+        Span s[2 * kEncEpg];
         uint8_t* tag_at[kEncEpg];
         uint32_t klen[kEncEpg], vlen[kEncEpg], type[kEncEpg], cnt[kEncEpg];
         uint64_t seq[kEncEpg];
@@ -193,20 +186,14 @@ __global__ __launch_bounds__(256) void k_enc_emit(const uint8_t* __restrict__ da
             vlen[j] = vlen_n[j];
             type[j] = type_n[j];
             const bool value = live[j] && type[j] == REVEL_TYPE_VALUE;
-            tag_at[j] = reps + (live[j] ? dst_n[j] & ~kEncFirstBit : 0u);
-            src[2 * j] = data + koff_n[j];
-            dst[2 * j] = tag_at[j] + 1u + varint_len(klen[j]);
-            len[2 * j] = live[j] ? klen[j] : 0u;
-            src[2 * j + 1] = data + voff_n[j];
-            dst[2 * j + 1] = dst[2 * j] + klen[j] + varint_len(vlen[j]);
-            len[2 * j + 1] = value ? vlen[j] : 0u;
+            const uint64_t tag = live[j] ? dst_n[j] & ~kEncFirstBit : 0u;
+            tag_at[j] = reps + tag;
+            s[2 * j] = {koff_n[j], tag + 1u + varint_len(klen[j]), live[j] ? klen[j] : 0u};
+            s[2 * j + 1] = {voff_n[j], s[2 * j].dst + klen[j] + varint_len(vlen[j]), value ? vlen[j] : 0u};
         }
-        if (base + waves * kVisit < n) fetch(base + waves * kVisit);
-        // tiny spans: every load of the group's spans, then the stores
+        if (base + stride < n) fetch(base + stride);
         TinyCopy c[2 * kEncEpg];
-#pragma unroll
-        for (uint32_t s = 0; s < 2 * kEncEpg; ++s)
-            tiny_load(src[s], dst[s], len[s] <= kTinyCopy ? len[s] : 0u, gl, safe, c[s]);
+        spans_load(data, reps, s, lane, safe, c);
         // tag + key-length varint (lanes 0..vk), value-length varint (lanes 0..vv-1): behind the loads
 #pragma unroll
         for (uint32_t j = 0; j < kEncEpg; ++j) {
@@ -218,24 +205,9 @@ __global__ __launch_bounds__(256) void k_enc_emit(const uint8_t* __restrict__ da
             }
             if (live[j] && gl <= vk) tag_at[j][gl] = gl == 0 ? (uint8_t)type[j] : varint_byte(klen[j], gl - 1u, vk);
             if (live[j] && type[j] == REVEL_TYPE_VALUE && gl < vv)
-                dst[2 * j][klen[j] + gl] = varint_byte(vlen[j], gl, vv);
+                reps[s[2 * j].dst + klen[j] + gl] = varint_byte(vlen[j], gl, vv);
         }
-#pragma unroll
-        for (uint32_t s = 0; s < 2 * kEncEpg; ++s)
-            if (len[s] <= kTinyCopy) tiny_store(src[s], dst[s], len[s], gl, c[s]);
-#pragma unroll
-        for (uint32_t s = 0; s < 2 * kEncEpg; ++s) {
-            if (len[s] > kTinyCopy && len[s] <= kSmallSpan) group_copy<8>(src[s], dst[s], len[s], gl);
-            // large spans: one bit per group (its lane 0), whole wave each
-            uint64_t big = __ballot(len[s] > kSmallSpan && gl == 0);
-            while (big) {
-                const uint32_t l = (uint32_t)__builtin_ctzll(big);
-                big &= big - 1;
-                const uint64_t so = __shfl((uint64_t)(src[s] - data), l, 64), dd = __shfl((uint64_t)(dst[s] - reps), l, 64);
-                const uint32_t ln = __shfl(len[s], l, 64);
-                group_copy<64>(data + so, reps + dd, ln, lane);
-            }
-        }
+        spans_finish(data, reps, s, lane, c);
     }
 }
 
@@ -269,10 +241,10 @@ hipError_t encode_emit(const DeviceInfo& di, const void* d_data, const revel_bat
                        d_err, cap, static_cast<uint8_t*>(d_reps), d_ent_dst, d_hdr_seq, d_hdr_n);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || nentries == 0) return e;
-    hipLaunchKernelGGL(k_enc_emit, dim3(grid_for(di, nentries, 4 * 8 * kEncEpg)), dim3(256), 0, st,
-                       static_cast<const uint8_t*>(d_data), d_entries, nentries, d_ent_dst, d_hdr_seq, d_hdr_n, d_roff + nbatches,
-                       d_err, cap,
-                       static_cast<uint8_t*>(d_reps));
+    using Visit = SpanVisit<kEncEpg>;
+    hipLaunchKernelGGL(k_enc_emit, dim3(Visit::grid(di, nentries)), dim3(Visit::kThreads), 0, st,
+                       static_cast<const uint8_t*>(d_data), d_entries, nentries, d_ent_dst, d_hdr_seq, d_hdr_n,
+                       d_roff + nbatches, d_err, cap, static_cast<uint8_t*>(d_reps));
     return hipGetLastError();
 }
 

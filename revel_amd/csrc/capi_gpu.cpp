@@ -30,6 +30,8 @@ int set_error(int code, const char* fmt, ...) {
 
 }  // namespace revel
 
+using revel::hip_fail;
+using revel::pick;
 using revel::set_error;
 
 namespace revel {
@@ -121,32 +123,11 @@ int default_context(revel_gpu_context** out) {
 
 namespace {
 
-int hip_fail(hipError_t e, const char* what) {
-    return set_error(REVEL_IO_ERROR, "%s: %s", what, hipGetErrorString(e));
-}
-
 bool is_gfx950(int dev) {
     hipDeviceProp_t p;
     if (hipGetDeviceProperties(&p, dev) != hipSuccess) return false;
     return strncmp(p.gcnArchName, "gfx950", 6) == 0;
 }
-
-hipStream_t pick(const revel_gpu_context* c, void* stream) {
-    return stream ? static_cast<hipStream_t>(stream) : c->stream;
-}
-
-// Validates the context and binds its device for the rest of the calling
-// function (restoring the caller's device on return).
-#define CHECK_CTX(ctx)                                                                     \
-    if (!(ctx)) return set_error(REVEL_INVALID_ARGUMENT, "null revel_gpu_context");        \
-    revel::DeviceGuard device_guard_((ctx)->di.device);                                     \
-    if (device_guard_.err() != hipSuccess) return hip_fail(device_guard_.err(), "hipSetDevice")
-
-#define HIP_TRY(expr, what)                          \
-    do {                                             \
-        hipError_t e_ = (expr);                      \
-        if (e_ != hipSuccess) return hip_fail(e_, what); \
-    } while (0)
 
 }  // namespace
 

@@ -627,4 +627,78 @@ __device__ __forceinline__ void tiny_store(const uint8_t* src, uint8_t* __restri
     }
 }
 
+// ---------------------------------------------------------------------------
+// The span-copy engine of the kernels that move variable-length byte spans
+// inside HBM (k_scatter_fragments, k_reasm_gather, k_enc_emit).  A wave visits
+// 8 FPG descriptors at a time, FPG per 8-lane group (descriptor base + 8 j +
+// grp), fetched one visit ahead; a descriptor becomes one or more spans, and a
+// group copies its N spans in three tiers:
+//   len <= kTinyCopy   spans_load: every load of all N spans is issued before
+//                      any store (the copy is latency-bound: with one ~131-B
+//                      span per group and visit a wave had 8 spans' bytes in
+//                      flight, profiles/r1s3_pmc_batches_summary.txt), then
+//                      spans_finish stores them;
+//   len <= kGroupCopy  group_copy<8>, one span after another;
+//   larger             one bit per group in a ballot, and the whole wave
+//                      copies each with group_copy<64>.
+// The two phases are separate calls so that a kernel can put stores of its
+// own (record headers, tags, varints) between them, behind the loads.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kGroupCopy = 1024;
+struct Span {
+    uint64_t src, dst;  // offsets from the kernel's source and destination base
+    uint32_t len;       // 0: nothing to copy (src and dst are then never dereferenced)
+};
+
+// safe: 4-B aligned, at least 4 readable bytes (where the idle lanes' loads go).
+template <uint32_t N>
+__device__ __forceinline__ void spans_load(const uint8_t* __restrict__ src, const uint8_t* dst, const Span (&s)[N],
+                                           uint32_t lane, const uint8_t* safe, TinyCopy (&c)[N]) {
+#pragma unroll
+    for (uint32_t j = 0; j < N; ++j)
+        tiny_load(src + s[j].src, dst + s[j].dst, s[j].len <= kTinyCopy ? s[j].len : 0u, lane & 7u, safe, c[j]);
+}
+template <uint32_t N>
+__device__ __forceinline__ void spans_finish(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
+                                             const Span (&s)[N], uint32_t lane, const TinyCopy (&c)[N]) {
+    const uint32_t gl = lane & 7u;
+#pragma unroll
+    for (uint32_t j = 0; j < N; ++j)
+        if (s[j].len <= kTinyCopy) tiny_store(src + s[j].src, dst + s[j].dst, s[j].len, gl, c[j]);
+#pragma unroll
+    for (uint32_t j = 0; j < N; ++j) {
+        if (s[j].len > kTinyCopy && s[j].len <= kGroupCopy) group_copy<8>(src + s[j].src, dst + s[j].dst, s[j].len, gl);
+        uint64_t big = __ballot(s[j].len > kGroupCopy && gl == 0);
+        while (big) {
+            const uint32_t l = (uint32_t)__builtin_ctzll(big);
+            big &= big - 1;
+            const uint64_t so = __shfl(s[j].src, l, 64), dd = __shfl(s[j].dst, l, 64);
+            const uint32_t ln = __shfl(s[j].len, l, 64);
+            group_copy<64>(src + so, dst + dd, ln, lane);
+        }
+    }
+}
+
+// Visit geometry for FPG descriptors per 8-lane group, in workgroups of
+// kThreads: what a wave takes per visit, where it starts and how far it steps,
+// and the launch grid for n descriptors.  The kernels are launched with
+// kThreads and do not read blockDim (a vector load and a wait on it ahead of
+// each wave's first descriptor fetch otherwise).
+template <uint32_t FPG>
+struct SpanVisit {
+    static constexpr uint32_t kThreads = 256;
+    static constexpr uint32_t kPerVisit = 64 / 8 * FPG;
+    static constexpr uint32_t kPerWorkgroup = kThreads / 64 * kPerVisit;
+    static uint32_t grid(const DeviceInfo& di, uint64_t n) {
+        return (uint32_t)std::max<uint64_t>(
+            1, std::min<uint64_t>((uint64_t)di.num_cu * 8, (n + kPerWorkgroup - 1) / kPerWorkgroup));
+    }
+    // descriptor j (< FPG) of this lane's group in the visit at `base`
+    __device__ static uint64_t index(uint64_t base, uint32_t j) { return base + 8u * j + (lane_id() >> 3); }
+    __device__ static uint64_t first() {
+        return (blockIdx.x * (uint64_t)(kThreads / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6)) * kPerVisit;
+    }
+    __device__ static uint64_t stride() { return (uint64_t)gridDim.x * kPerWorkgroup; }
+};
+
 }  // namespace

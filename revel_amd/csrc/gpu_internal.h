@@ -316,3 +316,26 @@ struct revel_gpu_context {
     int readers = 0;
     bool free_requested = false;
 };
+
+// The prologue of the C-ABI entry points that take a context.
+namespace revel {
+inline int hip_fail(hipError_t e, const char* what) {
+    return set_error(REVEL_IO_ERROR, "%s: %s", what, hipGetErrorString(e));
+}
+inline hipStream_t pick(const revel_gpu_context* c, void* stream) {
+    return stream ? static_cast<hipStream_t>(stream) : c->stream;
+}
+}  // namespace revel
+
+// Validates the context and binds its device for the rest of the calling
+// function (restoring the caller's device on return).
+#define CHECK_CTX(ctx)                                                                            \
+    if (!(ctx)) return revel::set_error(REVEL_INVALID_ARGUMENT, "null revel_gpu_context");        \
+    revel::DeviceGuard device_guard_((ctx)->di.device);                                            \
+    if (device_guard_.err() != hipSuccess) return revel::hip_fail(device_guard_.err(), "hipSetDevice")
+
+#define HIP_TRY(expr, what)                                     \
+    do {                                                        \
+        hipError_t e_ = (expr);                                 \
+        if (e_ != hipSuccess) return revel::hip_fail(e_, what); \
+    } while (0)

@@ -482,9 +482,8 @@ int revel_gpu_append_records(revel_gpu_context* ctx, const void* d_payloads, con
     if (len > image_cap) return set_error(REVEL_INVALID_ARGUMENT, "image capacity %zu < %llu", image_cap,
                                           (unsigned long long)len);
     if (len && (!d_image || (!d_payloads && frags.size()))) return set_error(REVEL_INVALID_ARGUMENT, "null device buffer");
-    revel::DeviceGuard guard(ctx->di.device);
-    if (guard.err() != hipSuccess) return set_error(REVEL_IO_ERROR, "hipSetDevice failed");
-    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+    CHECK_CTX(ctx);
+    hipStream_t st = revel::pick(ctx, stream);
     // Header lists for the device CRC pass: per virtual block (image byte 0 at
     // in-block offset `lead`) its record count and the fragment index of its
     // first record; the scatter kernel writes one entry per fragment.
@@ -525,7 +524,7 @@ int revel_gpu_append_records(revel_gpu_context* ctx, const void* d_payloads, con
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) {
         (void)hipStreamSynchronize(st);  // the context's scratch is free before the next call
-        return set_error(REVEL_IO_ERROR, "append_records: %s", hipGetErrorString(e));
+        return revel::hip_fail(e, "append_records");
     }
     *image_len = len;
     *block_offset = boff;

@@ -100,30 +100,24 @@ __global__ void k_reasm_emit(const revel_record_result* __restrict__ phys, uint6
     }
 }
 
-// Fragments of emitted logical records, 32 per wave visit, 4 per 8-lane
-// group.  Fragments of at most kTinyCopy bytes (small-record logs) are copied
-// by their group with all four fragments' loads issued before any store, so a
-// wave has 32 fragments' bytes in flight instead of 8 (the copy is latency-
-// bound: profiles/r1s3_pmc_batches_summary.txt); fragments of at most
-// kSmallFrag bytes then by their group one after another, larger ones one
-// after another by the whole wave.
-constexpr uint32_t kSmallFrag = 1024;
+// The fragments of emitted logical records, copied by the span engine of
+// device_common.h: fragment k's span is its payload, image[file_offset -
+// image_base + 7, + length) -> payload[frag_dst[k], + length); a fragment of
+// no emitted record (frag_dst ~0) is a dead span.
 constexpr uint32_t kGatherFpg = 4;  // fragments per 8-lane group and visit
 __global__ void k_reasm_gather(const uint8_t* __restrict__ image, uint64_t image_base,
                                const revel_record_result* __restrict__ phys, uint64_t n,
                                const uint64_t* __restrict__ frag_dst, uint8_t* __restrict__ payload) {
-    const uint32_t lane = lane_id(), grp = lane >> 3, gl = lane & 7u;
-    const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x / 64);
-    const uint64_t w0 = blockIdx.x * (uint64_t)(blockDim.x / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    constexpr uint64_t kVisit = 8u * kGatherFpg;
-    // descriptors one visit ahead (fragment base + 8 j + grp of a visit: each j
-    // reads 8 consecutive descriptors), clamped loads + a validity flag
+    using Visit = SpanVisit<kGatherFpg>;
+    const uint32_t lane = lane_id();
+    const uint64_t start = Visit::first(), stride = Visit::stride();
+    // descriptors one visit ahead: clamped loads, destination ~0 past the end
     uint64_t dst_n[kGatherFpg], off_n[kGatherFpg];
     uint32_t len_n[kGatherFpg];
     auto fetch = [&](uint64_t base) {
 #pragma unroll
         for (uint32_t j = 0; j < kGatherFpg; ++j) {
-            const uint64_t k = base + 8u * j + grp;
+            const uint64_t k = Visit::index(base, j);
             const uint64_t kc = k < n ? k : n - 1;
             const uint64_t d = frag_dst[kc];
             dst_n[j] = k < n ? d : ~0ull;
@@ -131,41 +125,16 @@ __global__ void k_reasm_gather(const uint8_t* __restrict__ image, uint64_t image
             len_n[j] = phys[kc].length;
         }
     };
-    if (w0 * kVisit < n) fetch(w0 * kVisit);
-    for (uint64_t base = w0 * kVisit; base < n; base += waves * kVisit) {
-        uint64_t dst[kGatherFpg], src_off[kGatherFpg];
-        uint32_t len[kGatherFpg];
-#pragma unroll
-        for (uint32_t j = 0; j < kGatherFpg; ++j) {
-            dst[j] = dst_n[j];
-            src_off[j] = off_n[j] - image_base + kHeaderSize;
-            len[j] = len_n[j];
-        }
-        if (base + waves * kVisit < n) fetch(base + waves * kVisit);
-        // tiny fragments: every load of the group's four, then the stores
-        TinyCopy c[kGatherFpg];
-#pragma unroll
-        for (uint32_t j = 0; j < kGatherFpg; ++j) {
-            const bool tiny = dst[j] != ~0ull && len[j] <= kTinyCopy;
-            tiny_load(image + src_off[j], payload + (tiny ? dst[j] : 0u), tiny ? len[j] : 0u, gl, image, c[j]);
-        }
+    if (start < n) fetch(start);
+    for (uint64_t base = start; base < n; base += stride) {
+        Span s[kGatherFpg];
 #pragma unroll
         for (uint32_t j = 0; j < kGatherFpg; ++j)
-            if (dst[j] != ~0ull && len[j] <= kTinyCopy) tiny_store(image + src_off[j], payload + dst[j], len[j], gl, c[j]);
-#pragma unroll
-        for (uint32_t j = 0; j < kGatherFpg; ++j) {
-            const bool small = dst[j] != ~0ull && len[j] > kTinyCopy && len[j] <= kSmallFrag;
-            if (small) group_copy<8>(image + src_off[j], payload + dst[j], len[j], gl);
-            // large fragments: one bit per group (its lane 0), whole wave each
-            uint64_t big = __ballot(dst[j] != ~0ull && len[j] > kSmallFrag && gl == 0);
-            while (big) {
-                const uint32_t l = (uint32_t)__builtin_ctzll(big);
-                big &= big - 1;
-                const uint64_t so = __shfl(src_off[j], l, 64), dd = __shfl(dst[j], l, 64);
-                const uint32_t ln = __shfl(len[j], l, 64);
-                group_copy<64>(image + so, payload + dd, ln, lane);
-            }
-        }
+            s[j] = {off_n[j] - image_base + kHeaderSize, dst_n[j], dst_n[j] != ~0ull ? len_n[j] : 0u};
+        if (base + stride < n) fetch(base + stride);
+        TinyCopy c[kGatherFpg];
+        spans_load(image, payload, s, lane, image, c);
+        spans_finish(image, payload, s, lane, c);
     }
 }
 
@@ -217,9 +186,10 @@ hipError_t reasm_emit(const DeviceInfo& di, const revel_record_result* d_phys, u
 hipError_t reasm_gather(const DeviceInfo& di, const void* d_image, uint64_t image_base,
                         const revel_record_result* d_phys, uint64_t n, const uint64_t* d_frag_dst, void* d_payload,
                         hipStream_t st) {
-    const uint64_t grid = std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)di.num_cu * 8, (n + 127) / 128));
-    hipLaunchKernelGGL(k_reasm_gather, dim3((uint32_t)grid), dim3(256), 0, st, static_cast<const uint8_t*>(d_image),
-                       image_base, d_phys, n, d_frag_dst, static_cast<uint8_t*>(d_payload));
+    using Visit = SpanVisit<kGatherFpg>;
+    hipLaunchKernelGGL(k_reasm_gather, dim3(Visit::grid(di, n)), dim3(Visit::kThreads), 0, st,
+                       static_cast<const uint8_t*>(d_image), image_base, d_phys, n, d_frag_dst,
+                       static_cast<uint8_t*>(d_payload));
     return hipGetLastError();
 }
 

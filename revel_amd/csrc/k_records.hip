@@ -1011,48 +1011,44 @@ constexpr int kRowsRing = REVEL_ROWS_RING;  // rows in flight per wave in k_veri
 // layout comes from the host (frame_layout()).
 // ---------------------------------------------------------------------------
 // FPG = fragments per 8-lane group and wave visit: 3 for small-record
-// batches, 1 when fragments average over 1 KiB (whole-wave copies then get
-// more waves instead of longer visits)
+// batches, 1 when fragments average over kGroupCopy bytes (whole-wave copies
+// then get more waves instead of longer visits)
 template <uint32_t kScatterFpg>
 __global__ void k_scatter_fragments(const uint8_t* __restrict__ payloads, const revel::FragDesc* __restrict__ frags,
                                     uint64_t nfrags, uint8_t* __restrict__ image, uint64_t* __restrict__ xlist) {
-    // 8 FPG fragments per wave visit, FPG per 8-lane group (fragment base +
-    // 8 j + grp): payloads of at most kTinyCopy bytes are copied with all of
-    // the group's loads issued before any store (the copy is latency-bound:
-    // profiles/r1s3_pmc_batches_summary.txt), up to kSmallFragment bytes by
-    // the group one after another, larger ones by the whole wave
-    constexpr uint32_t kSmallFragment = 1024;
-    constexpr uint64_t kVisit = 8u * kScatterFpg;
-    const uint32_t lane = lane_id(), grp = lane >> 3, gl = lane & 7u;
-    const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x / 64);
-    const uint64_t w0 = blockIdx.x * (uint64_t)(blockDim.x / 64) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    // Copied by the span engine of device_common.h: a record fragment's span
+    // is its payload, payloads[src, + len) -> image[dst + 7, + len); a trailer
+    // (and a slot past the last fragment) is a dead span.
+    using Visit = SpanVisit<kScatterFpg>;
+    const uint32_t lane = lane_id(), gl = lane & 7u;
+    const uint64_t start = Visit::first(), stride = Visit::stride();
     // descriptors one visit ahead (clamped loads: no branch around a load)
     revel::FragDesc dn[kScatterFpg];
     auto fetch = [&](uint64_t base) {
 #pragma unroll
         for (uint32_t j = 0; j < kScatterFpg; ++j) {
-            const uint64_t k = base + 8u * j + grp;
+            const uint64_t k = Visit::index(base, j);
             dn[j] = frags[k < nfrags ? k : nfrags - 1];
         }
     };
-    if (w0 * kVisit < nfrags) fetch(w0 * kVisit);
-    for (uint64_t base = w0 * kVisit; base < nfrags; base += waves * kVisit) {
+    if (start < nfrags) fetch(start);
+    for (uint64_t base = start; base < nfrags; base += stride) {
         revel::FragDesc d[kScatterFpg];
 #pragma unroll
         for (uint32_t j = 0; j < kScatterFpg; ++j) d[j] = dn[j];
-        if (base + waves * kVisit < nfrags) fetch(base + waves * kVisit);
-        bool live[kScatterFpg], pay[kScatterFpg];
-        TinyCopy c[kScatterFpg];
+        if (base + stride < nfrags) fetch(base + stride);
+        Span s[kScatterFpg];
+        bool live[kScatterFpg];
 #pragma unroll
         for (uint32_t j = 0; j < kScatterFpg; ++j) {
-            live[j] = base + 8u * j + grp < nfrags;
-            pay[j] = live[j] && d[j].type != revel::kTrailer;
-            const bool tiny = pay[j] && d[j].len <= kTinyCopy;
-            tiny_load(payloads + d[j].src, image + d[j].dst + kHeaderSize, tiny ? d[j].len : 0u, gl, image, c[j]);
+            live[j] = Visit::index(base, j) < nfrags;
+            s[j] = {d[j].src, d[j].dst + kHeaderSize, live[j] && d[j].type != revel::kTrailer ? d[j].len : 0u};
         }
+        TinyCopy c[kScatterFpg];
+        spans_load(payloads, image, s, lane, image, c);
+        // header bytes (CRC left zero) and trailer zeros: behind the loads
 #pragma unroll
         for (uint32_t j = 0; j < kScatterFpg; ++j) {
-            const uint64_t f = base + 8u * j + grp;
             uint8_t* dst = image + d[j].dst;
             if (live[j]) {
                 if (d[j].type == revel::kTrailer) {
@@ -1061,24 +1057,11 @@ __global__ void k_scatter_fragments(const uint8_t* __restrict__ payloads, const 
                     const uint32_t hv = gl < 4 ? 0u : gl == 4 ? (d[j].len & 0xffu) : gl == 5 ? (d[j].len >> 8) : d[j].type;
                     dst[gl] = (uint8_t)hv;
                     // header-list entry of this record for the CRC pass (CRC still 0)
-                    if (gl == 0 && xlist) xlist[f] = list_entry(Hdr{0u, d[j].len, d[j].type});
+                    if (gl == 0 && xlist) xlist[Visit::index(base, j)] = list_entry(Hdr{0u, d[j].len, d[j].type});
                 }
             }
-            if (pay[j] && d[j].len <= kTinyCopy) tiny_store(payloads + d[j].src, dst + kHeaderSize, d[j].len, gl, c[j]);
         }
-#pragma unroll
-        for (uint32_t j = 0; j < kScatterFpg; ++j) {
-            const bool small = pay[j] && d[j].len > kTinyCopy && d[j].len <= kSmallFragment;
-            if (small) group_copy<8>(payloads + d[j].src, image + d[j].dst + kHeaderSize, d[j].len, gl);
-            uint64_t big = __ballot(pay[j] && d[j].len > kSmallFragment && gl == 0);
-            while (big) {
-                const uint32_t l = (uint32_t)__builtin_ctzll(big);
-                big &= big - 1;
-                const uint64_t so = __shfl(d[j].src, l, 64), dd = __shfl(d[j].dst, l, 64);
-                const uint32_t ln = __shfl(d[j].len, l, 64);
-                group_copy<64>(payloads + so, image + dd + kHeaderSize, ln, lane);
-            }
-        }
+        spans_finish(payloads, image, s, lane, c);
     }
 }
 
@@ -1439,18 +1422,14 @@ hipError_t frame_records(const DeviceInfo& di, const void* d_payloads, const Fra
                          void* d_image, uint64_t image_len, uint32_t lead, hipStream_t st, const uint32_t* d_counts,
                          const uint32_t* d_first, uint64_t* d_xlist, uint32_t* d_blist) {
     if (nfrags) {
-        const bool small = image_len / nfrags <= 1024u;
-        const uint64_t per_wg = small ? 96 : 32;  // 4 waves x 8 groups x FPG
-        const uint64_t grid =
-            std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)di.num_cu * 8, (nfrags + per_wg - 1) / per_wg));
-        if (small)
-            hipLaunchKernelGGL(k_scatter_fragments<3>, dim3((uint32_t)grid), dim3(256), 0, st,
-                               static_cast<const uint8_t*>(d_payloads), d_frags, nfrags, static_cast<uint8_t*>(d_image),
-                               d_xlist);
+        if (image_len / nfrags <= kGroupCopy)
+            hipLaunchKernelGGL(k_scatter_fragments<3>, dim3(SpanVisit<3>::grid(di, nfrags)), dim3(SpanVisit<3>::kThreads),
+                               0, st, static_cast<const uint8_t*>(d_payloads), d_frags, nfrags,
+                               static_cast<uint8_t*>(d_image), d_xlist);
         else
-            hipLaunchKernelGGL(k_scatter_fragments<1>, dim3((uint32_t)grid), dim3(256), 0, st,
-                               static_cast<const uint8_t*>(d_payloads), d_frags, nfrags, static_cast<uint8_t*>(d_image),
-                               d_xlist);
+            hipLaunchKernelGGL(k_scatter_fragments<1>, dim3(SpanVisit<1>::grid(di, nfrags)), dim3(SpanVisit<1>::kThreads),
+                               0, st, static_cast<const uint8_t*>(d_payloads), d_frags, nfrags,
+                               static_cast<uint8_t*>(d_image), d_xlist);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }

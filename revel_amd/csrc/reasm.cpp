@@ -66,11 +66,9 @@ extern "C" int revel_gpu_reassemble(revel_gpu_context* ctx, const void* d_image,
     *payload_bytes = 0;
     if (nphys == 0) return REVEL_OK;
     if (!d_image || !d_phys || !d_out || !d_payload) return set_error(REVEL_INVALID_ARGUMENT, "null device buffer");
-    revel::DeviceGuard guard(ctx->di.device);
-    if (guard.err() != hipSuccess) return set_error(REVEL_IO_ERROR, "hipSetDevice failed");
-    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
-    hipError_t e = revel::reassemble_events(ctx, d_image, image_base, image_base + image_len, d_phys, nphys, checksum,
-                                            d_out, d_payload, nlogical, payload_bytes, st);
-    if (e != hipSuccess) return set_error(REVEL_IO_ERROR, "reassemble: %s", hipGetErrorString(e));
+    CHECK_CTX(ctx);
+    HIP_TRY(revel::reassemble_events(ctx, d_image, image_base, image_base + image_len, d_phys, nphys, checksum, d_out,
+                                     d_payload, nlogical, payload_bytes, revel::pick(ctx, stream)),
+            "reassemble");
     return REVEL_OK;
 }

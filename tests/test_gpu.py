@@ -600,7 +600,9 @@ def test_replay_file_io_methods(gpu_ctx, tmp_path, io):
 @pytest.mark.parametrize("block_offset", [0, 1, 6, 7, 100, 32760, 32761, 32762, 32767, 32768])
 def test_append_records_matches_writer(gpu_ctx, block_offset):
     rng = np.random.default_rng(block_offset + 1)
-    sizes = list(rng.integers(0, 3000, 40)) + [0, 0, 32761, 32754, 70000, 1, 5] + list(rng.integers(0, 100, 300))
+    # the fixed middle list has both sides of the copy tiers' bounds (140 and 1024 bytes)
+    sizes = (list(rng.integers(0, 3000, 40)) + [0, 0, 32761, 32754, 70000, 1, 5, 139, 140, 141, 1023, 1024, 1025]
+             + list(rng.integers(0, 100, 300)))
     recs = [rng.integers(0, 256, int(s), dtype=np.uint8).tobytes() for s in sizes]
     blob = np.frombuffer(b"".join(recs), dtype=np.uint8)
     d = gpu_ctx.upload(blob if blob.size else np.zeros(1, np.uint8))
@@ -724,11 +726,16 @@ def test_reassemble_golden(gpu_ctx, golden_index, checksum):
 
 def test_reassemble_gather_alignments(gpu_ctx):
     """Every payload length 0..99 plus 33-B multiples, so fragments start and
-    end at every offset mod 16 in the image and in the gathered buffer."""
+    end at every offset mod 16 in the image and in the gathered buffer, and
+    the lengths on both sides of the copy tiers' bounds (140 and 1024 bytes)
+    as whole fragments."""
     rng = np.random.default_rng(32)
-    sizes = list(range(100)) + [33 * k for k in range(1, 40)] + [32761, 32762, 40000, 65536]
+    edges = [139, 140, 141, 1023, 1024, 1025]
+    sizes = list(range(100)) + [33 * k for k in range(1, 40)] + [32761, 32762, 40000, 65536] + edges
     rng.shuffle(sizes)
     recs = [rng.integers(0, 256, int(s), dtype=np.uint8).tobytes() for s in sizes]
+    # no edge length may be lost to a record split at a block boundary
+    assert set(edges) <= set(int(n) for n in oc.walk(oc.write_image(recs, 0))["length"])
     for boff in (0, 5):
         check_reassembly(gpu_ctx, oc.write_image(recs, boff) if boff == 0 else oc.write_image(recs), True)
 
